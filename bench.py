@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the MI355X macroblock engine on BASELINE.json's metric ("Measurement").
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A *step* is one pass of the hot path (mode decision + reconstruction, in-loop deblocking, border expansion) over one
 batch: `--sessions` independent 1080p pictures per GPU (default 128 = two slice workgroups per CU), every session with its
@@ -10,8 +10,14 @@ own content, sources already resident in HBM, MB records left in HBM.  value = p
 With --gpus N > 1 and no torchrun environment the script launches the N ranks itself (one process per GPU, sessions
 sharded over ranks, no data-path collective: "weak" scaling); under torchrun it is one of the ranks.
 
+A plain run only sets up, warms up, times the K steps (ms_per_step = wall time of the timed steps / K), writes the outputs of the last
+timed step if --dump-outputs is given, and prints the line.  --dump-outputs DIR: the reconstructed pictures (what a caller of the hot path
+reads back, WelsHipGroupGetReconFrame) of a fixed sample of sessions spread over the batch, as DIR/recon_y.npy, recon_u.npy, recon_v.npy
+(float32, sessions x rows x columns, at most 64 MB in all) and DIR/sessions.npy (the sampled session indices, float64).
+
 The JSON line (last line of stdout, rank 0) carries, besides the contract's keys:
   roofline       dominant kernel, algorithmic bytes per launch / HIP-event launch time (events on the launch stream)
+With --full it also carries (each leg takes runs of its own):
   verified       the reconstructions the timed steps left behind (eight sessions spread over 0 .. N-1) equal the reference decoder's output of
                  the reference encoder's stream for the same frame order (oracle/_ref, run live) -- the run fails otherwise
   e2e_pipelined  complete EncodeFrame rate incl. source upload, D2H of the packed MB records and host CAVLC (the PCIe/host-inclusive
@@ -41,6 +47,7 @@ BYTES_I_MB_MD = 384 + 384 + 960  # the mode-decision/reconstruction kernel's sha
 BYTES_P_MB_PATH = 2912
 BYTES_P_MB_MD = 384 + 384 + 384 + 960 + 32
 REF_DIR = os.path.join(ROOT, "oracle", "_ref")
+DUMP_BYTES = 60 * 1000 * 1000    # --dump-outputs: bytes of float32 samples at most
 RES_DIR = os.path.join(REF_DIR, "res")
 
 
@@ -56,13 +63,18 @@ def parse():
     ap.add_argument("--qp", type=int, default=24)
     ap.add_argument("--workload", default="p", choices=["intra", "p"])
     ap.add_argument("--content", default="synthetic", choices=["synthetic", "res"], help="res: the reference's own clip of that size (oracle/_ref/res)")
-    ap.add_argument("--quick", action="store_true", help="only the headline leg (no e2e / latency / res clip / intra / cpu baseline / verification)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beyond the headline figure: verification against oracle/_ref, e2e / latency / res clip / intra / configs 4 and 5 / "
+                         "cpu baseline legs, and with --gpus N > 1 the multi-GPU legs")
+    ap.add_argument("--quick", action="store_true", help="only the headline leg (what a plain run does; overrides --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the reconstructions of a fixed sample of sessions (the last timed step's) as DIR/*.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-verify", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the e2e, latency, res-clip and intra legs")
     ap.add_argument("--host-threads", type=int, default=min(32, os.cpu_count() or 8))
     ap.add_argument("--multi-gpu-legs", action="store_true",
-                    help="with --gpus N > 1: also run BASELINE configs 4 and 5 across the ranks (default there unless --quick; the launcher test asks for them explicitly)")
+                    help="with --gpus N > 1: also run BASELINE configs 4 and 5 across the ranks (default there with --full; the launcher test asks for them explicitly)")
     ap.add_argument("--cpu-launcher-test", action="store_true",
                     help="TEST ONLY (tests/test_multi_rank.py): exercise the N-rank launch / barrier / max-over-ranks / JSON logic without a GPU -- "
                          "gloo instead of RCCL, WELSHIP_LIB must name the CPU test build of the kernels; implies --quick, the line is marked as no measurement")
@@ -71,6 +83,8 @@ def parse():
     if a.cpu_launcher_test:
         a.quick = True
     if a.quick:
+        a.full = False
+    if not a.full:
         a.no_cpu_baseline = a.no_verify = a.no_extra = True
     return a
 
@@ -153,6 +167,22 @@ def ref_decode_last_frame(bs, w, h):
         with open(fo, "rb") as f:
             f.seek(-fsz, 2)
             return f.read()
+
+
+def dump_outputs(d, recons, w, h):
+    """The reconstructions of the sampled sessions as float32 planes (sessions x rows x columns) + the session indices, at most DUMP_BYTES."""
+    import numpy as np
+    sessions = sorted(recons)
+    pics = np.stack([np.frombuffer(recons[s], dtype=np.uint8) for s in sessions])
+    planes = {"recon_y": pics[:, :w * h].reshape(-1, h, w),
+              "recon_u": pics[:, w * h:w * h * 5 // 4].reshape(-1, h // 2, w // 2),
+              "recon_v": pics[:, w * h * 5 // 4:].reshape(-1, h // 2, w // 2)}
+    if pics.size * 4 > DUMP_BYTES:             # (one picture above the budget: the top rows of its luma plane only)
+        planes = {"recon_y": planes["recon_y"][:, :DUMP_BYTES // (4 * w)]}
+    os.makedirs(d, exist_ok=True)
+    for name, v in planes.items():
+        np.save(os.path.join(d, name + ".npy"), v.astype(np.float32))
+    np.save(os.path.join(d, "sessions.npy"), np.array(sessions, dtype=np.float64))
 
 
 def spread_sessions(n, k):
@@ -238,9 +268,9 @@ def make_group(oh, a, local, w, h, workload, sessions, ring, content, idc=None, 
     return g
 
 
-def hot_path_leg(oh, a, local, w, h, workload, sessions, ring, content, steps, warmup, barrier=None, verify_sessions=()):
+def hot_path_leg(oh, a, local, w, h, workload, sessions, ring, content, steps, warmup, barrier=None, verify_sessions=(), keep_sessions=()):
     """IDR (P workload) + warmup + `steps` timed device-only steps.  Returns (wall seconds of the timed steps, event dict,
-    verification result or None)."""
+    verification result or None); hot_path_leg.recons = the last timed step's reconstruction of every session of `keep_sessions`."""
     g = make_group(oh, a, local, w, h, workload, sessions, ring, content)
     order = []                                       # source slots in coding order (the reference is fed the same frames)
     if workload == "p":
@@ -259,6 +289,7 @@ def hot_path_leg(oh, a, local, w, h, workload, sessions, ring, content, steps, w
         barrier()
     dt = time.perf_counter() - t0
     order += [slot_of(i, ring) for i in range(steps)]
+    hot_path_leg.recons = {s: g.recon(s) for s in keep_sessions}
     verified = None
     if verify_sessions:
         def check(s):
@@ -495,13 +526,16 @@ def main():
         data = "synthetic"
 
     verify_sessions = () if (a.no_verify or not have_ref or rank != 0) else spread_sessions(a.sessions, 8)
-    dt, ev, verified = hot_path_leg(oh, a, dev, w, h, workload, a.sessions, ring, content, a.steps, a.warmup, barrier, verify_sessions)
+    dump_sessions = () if (a.dump_outputs is None or rank != 0) else spread_sessions(a.sessions, max(1, min(4, DUMP_BYTES // (4 * fsz))))
+    dt, ev, verified = hot_path_leg(oh, a, dev, w, h, workload, a.sessions, ring, content, a.steps, a.warmup, barrier, verify_sessions, dump_sessions)
+    if dump_sessions:
+        dump_outputs(a.dump_outputs, hot_path_leg.recons, w, h)
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     mg = {}
-    if dist is not None and world > 1 and (a.multi_gpu_legs or not a.quick) and os.path.exists(os.path.join(REF_DIR, "ref_enc_hip")):
+    if dist is not None and world > 1 and (a.multi_gpu_legs or a.full) and os.path.exists(os.path.join(REF_DIR, "ref_enc_hip")):
         mg = multi_gpu_legs(rank, world, dev, dist, cpu_test, visible0)
     if rank != 0:
         if dist is not None:
@@ -538,7 +572,7 @@ def main():
     line = {
         "metric": json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"],
         "metric_scope": "value = device hot path (MD + reconstruction + deblocking + border expansion), entropy coding on the host excluded; "
-                        "`verified` = the timed steps' reconstruction equals the reference's, `e2e_pipelined` = complete EncodeFrame rate with a bitstream SHA1 check",
+                        "with --full, `verified` = the timed steps' reconstruction equals the reference's, `e2e_pipelined` = complete EncodeFrame rate with a bitstream SHA1 check",
         "value": pics / dt, "unit": "frames/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
         "ms_per_step": dt / a.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
         "dtype": "u8", "data": data if not cpu_test else data + " -- LAUNCHER TEST on the CPU test build of the kernels: not a measurement",

@@ -5,7 +5,7 @@
 # stages
 #   tier            the GPU tier exactly as the driver runs it (serial, -x) -> pytest_gpu.txt
 #   tier_all        the same without -x (every failure of the tier in one run)
-#   bench           the default bench line -> bench_default.json (+ a digest)
+#   bench           the bench line with every leg (bench.py --full) -> bench_default.json (+ a digest)
 #   quick           bench.py --quick (the timed configuration only) -> bench_quick.json
 #   stats           rocprofv3 --kernel-trace --stats of `bench.py --quick --steps 20 --warmup 5` (the driver's run shape) -> kernel_stats.csv
 #   pmc             FETCH_SIZE / WRITE_SIZE passes of `bench.py --quick` (separate runs, --kernel-trace only beside --pmc) -> pmc_traffic.txt
@@ -50,7 +50,7 @@ for stage in "$@"; do
   case $stage in
   tier)     WELSHIP_REQUIRE_ORACLE=1 timeout 1800 python -m pytest tests -m gpu -x -q > $o/pytest_gpu.txt 2>&1; tail -5 $o/pytest_gpu.txt | cut -c1-300; lap "gpu tier (serial, -x, as the driver runs it)";;
   tier_all) WELSHIP_REQUIRE_ORACLE=1 timeout 1800 python -m pytest tests -m gpu -q > $o/pytest_gpu_all.txt 2>&1; tail -15 $o/pytest_gpu_all.txt | cut -c1-300; lap "gpu tier (serial, every failure)";;
-  bench)    timeout 900 python bench.py > $o/bench_default.json 2> $o/bench_default.err; digest $o/bench_default.json; lap "bench default";;
+  bench)    timeout 900 python bench.py --full > $o/bench_default.json 2> $o/bench_default.err; digest $o/bench_default.json; lap "bench default";;
   quick)    timeout 300 python bench.py --quick > $o/bench_quick.json 2> $o/bench_quick.err; digest $o/bench_quick.json; lap "bench --quick";;
   stats)    ( cd /tmp && timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OLDPWD/$o/stats -- python $OLDPWD/bench.py --quick --steps 20 --warmup 5 > $OLDPWD/$o/prof_bench.json 2> $OLDPWD/$o/prof_bench.err )
             f=$(find $o/stats -name "*kernel_stats.csv" | head -1); cp $f $o/kernel_stats.csv 2>/dev/null; head -14 $o/kernel_stats.csv | cut -c1-200

@@ -89,7 +89,11 @@ typedef struct WelsHipEncParam {
                                        has no host slice threads; the field only reproduces what the reference does to the
                                        STREAM when it runs slice threads: deblocking across slice edges is switched off
                                        (idc 0 -> 2) because slices are filtered concurrently (encoder_ext.cpp:2051-2055)   */
-  int32_t reserved[6];
+  /* Per-picture quality statistic (SEncParamExt::bPsnrY / U / V, codec_app_def.h:595-597): for every picture, the sum of squared
+     differences between the source and the final reconstruction of each plane flagged here, computed on the device, and the reference's PSNR of it (WelsCalcPsnr, codec/common/src/utils.cpp:101-125) -- WelsHipGetFrameQuality /
+     WelsHipGroupGetFrameQuality.  ORed with WELSHIP_OPTION_PSNR_PLANES.  All zero: no extra device pass, nothing extra is copied. */
+  int32_t bPsnrY, bPsnrU, bPsnrV;
+  int32_t reserved[3];
   uint32_t uiSliceMbNum[35];        /* SM_RASTER_SLICE: macroblocks per slice (sSliceArgument.uiSliceMbNum, MAX_SLICES_NUM
                                        entries); uiSliceMbNum[0] == 0 = one slice per macroblock row                  */
 } WelsHipEncParam;
@@ -152,8 +156,25 @@ int  WelsHipGetReconFrame (WelsHipEncoder* pEncoder, uint8_t* pDstI420, size_t u
 #define WELSHIP_OPTION_TRACE_LEVEL 21
 #define WELSHIP_OPTION_TRACE_CALLBACK 22
 #define WELSHIP_OPTION_TRACE_CALLBACK_CONTEXT 23
+/* Engine-private (far above the reference's ENCODER_OPTION ids): the planes whose quality statistic the NEXT pictures get, an int bit mask
+ * 1 = Y, 2 = U, 4 = V (0..7), ORed with the bPsnr* fields of the parameters -- what SSourcePicture::bPsnrY / U / V request per picture in
+ * the reference (codec_app_def.h:666-668).  GetOption returns the mask last set. */
+#define WELSHIP_OPTION_PSNR_PLANES 0x10000
 int  WelsHipSetOption (WelsHipEncoder* pEncoder, int eOptionId, void* pOption);
 int  WelsHipGetOption (WelsHipEncoder* pEncoder, int eOptionId, void* pOption);
+/* Quality statistic of one picture: per plane Y, U, V the sum of squared differences between the source and the final (deblocked)
+ * reconstruction, and the PSNR the reference reports for it in
+ * SLayerBSInfo::rPsnr (codec_app_def.h:641; CALC_PSNR, codec/common/src/utils.cpp:77-80, 99.99 for a lossless plane) -- bit for bit.
+ * The area is the reference's: the picture rounded up to whole macroblocks (its iVideoWidth x iVideoHeight, param_svc.h:486-489), so a
+ * cropped picture is measured together with its padding (source: luma 0, chroma 128), chroma half of that.
+ * uiPlanes: the planes that were measured (bit 0 Y, 1 U, 2 V); the others report 0 and 0.0. */
+typedef struct WelsHipFrameQuality {
+  uint64_t uiSse[3];
+  float rPsnr[3];
+  uint32_t uiPlanes;
+} WelsHipFrameQuality;
+/* the picture of the last successful WelsHipEncodeFrame; cmInitParaError before the first one */
+int  WelsHipGetFrameQuality (WelsHipEncoder* pEncoder, WelsHipFrameQuality* pQuality);
 /* Name of the device backend in use ("hip:gfx950 ..."). */
 const char* WelsHipBackendName (WelsHipEncoder* pEncoder);
 const char* WelsHipGetLastError (void);
@@ -187,8 +208,13 @@ int  WelsHipGroupRunDevice (WelsHipEncoderGroup* pGroup, int bWait);
 int  WelsHipGroupFinish (WelsHipEncoderGroup* pGroup, WelsHipFrameBSInfo* pBsInfos);
 int  WelsHipGroupStepDeviceOnly (WelsHipEncoderGroup* pGroup, int iSlot);
 int  WelsHipGroupGetReconFrame (WelsHipEncoderGroup* pGroup, int iSession, uint8_t* pDstI420, size_t uiDstBytes);
+/* the quality statistic (WelsHipFrameQuality, above) of every session's picture of the step whose bitstreams the last WelsHipGroupEncodeFrames,
+ * WelsHipGroupFinish or finished WelsHipGroupEncodeFramesPipelined (*pbFinished = 1) returned: pQuality[iSessions].  The planes are the
+ * parameters' bPsnr* flags; one device pass per launch chunk, 24 bytes per picture copied back.  cmInitParaError before the first step. */
+int  WelsHipGroupGetFrameQuality (WelsHipEncoderGroup* pGroup, WelsHipFrameQuality* pQuality);
 const char* WelsHipGroupBackendName (WelsHipEncoderGroup* pGroup);
-/* hot-path timing with HIP events on the launch stream; pOutMs[4] = total, MD, deblock, expand */
+/* hot-path timing with HIP events on the launch stream; pOutMs[4] = total, MD, deblock, expand (total includes the quality pass when the
+ * parameters request one) */
 int  WelsHipGroupBench (WelsHipEncoderGroup* pGroup, int iSteps, int iWarmup, double* pOutMs);
 /* host share of the complete frame steps (EncodeFrames / Finish) so far, thread time per picture: pOut[4] = staging copy of
  * the source into page-locked memory (ms), entropy coding + NAL packing from the packed records (ms), pictures coded,

@@ -33,6 +33,7 @@ struct Api {
   int (*EncodeParameterSets) (WelsHipEncoder*, WelsHipFrameBSInfo*) = nullptr;
   int (*GetOption) (WelsHipEncoder*, int, void*) = nullptr;
   const char* (*GetLastError) (void) = nullptr;
+  int (*GetFrameQuality) (WelsHipEncoder*, WelsHipFrameQuality*) = nullptr;
   bool load() {
     if (so) return true;
     const char* path = getenv ("WELSHIP_LIB");
@@ -43,6 +44,7 @@ struct Api {
     SYM (InitializeExt, "WelsHipInitializeExt") SYM (Uninitialize, "WelsHipUninitialize") SYM (EncodeFrame, "WelsHipEncodeFrame")
     SYM (ForceIntraFrame, "WelsHipForceIntraFrame") SYM (GetLastError, "WelsHipGetLastError") SYM (GetReconFrame, "WelsHipGetReconFrame")
     SYM (SetOption, "WelsHipSetOption") SYM (GetOption, "WelsHipGetOption") SYM (EncodeParameterSets, "WelsHipEncodeParameterSets")
+    SYM (GetFrameQuality, "WelsHipGetFrameQuality")
 #undef SYM
     return true;
   }
@@ -85,6 +87,8 @@ class CWelsHipEncoder : public ISVCEncoder {
     q.bEnableSceneChangeDetect = p->bEnableSceneChangeDetect; q.bEnableLongTermReference = p->bEnableLongTermReference;
     q.bEnableDenoise = p->bEnableDenoise; q.bEnableFrameSkip = p->bEnableFrameSkip;
     q.iMultipleThreadIdc = p->iMultipleThreadIdc;
+    q.bPsnrY = p->bPsnrY; q.bPsnrU = p->bPsnrU; q.bPsnrV = p->bPsnrV;
+    m_param_planes = (p->bPsnrY ? 1 : 0) | (p->bPsnrU ? 2 : 0) | (p->bPsnrV ? 4 : 0);
     const int rc = g_api.InitializeExt (m_p, &q);
     if (rc) fprintf (stderr, "welship_isvc: InitializeExt: %s\n", g_api.GetLastError());
     m_w = p->iPicWidth; m_h = p->iPicHeight; m_frames = 0;
@@ -115,6 +119,11 @@ class CWelsHipEncoder : public ISVCEncoder {
     sp.iColorFormat = s->iColorFormat;
     for (int k = 0; k < 4; ++k) { sp.iStride[k] = s->iStride[k]; sp.pData[k] = s->pData[k]; }
     sp.iPicWidth = s->iPicWidth; sp.iPicHeight = s->iPicHeight; sp.uiTimeStamp = s->uiTimeStamp;
+    // the quality statistic of this picture: the planes the parameters ask for (measured, as the reference computes them for its statistics)
+    // and the ones the picture asks for -- only the latter are reported in rPsnr (encoder_ext.cpp:3918-3970)
+    const int pic_planes = (s->bPsnrY ? 1 : 0) | (s->bPsnrU ? 2 : 0) | (s->bPsnrV ? 4 : 0);
+    int planes = m_param_planes | pic_planes;
+    if (g_api.SetOption (m_p, WELSHIP_OPTION_PSNR_PLANES, &planes)) return cmInitParaError;
     WelsHipFrameBSInfo b;
     const int rc = g_api.EncodeFrame (m_p, &sp, &b);
     if (rc) { fprintf (stderr, "welship_isvc: EncodeFrame: %s\n", g_api.GetLastError()); return rc; }
@@ -127,6 +136,14 @@ class CWelsHipEncoder : public ISVCEncoder {
       o->sLayerInfo[i].uiQualityId = b.sLayerInfo[i].uiQualityId; o->sLayerInfo[i].iSubSeqId = b.sLayerInfo[i].iSubSeqId;
       o->sLayerInfo[i].iNalCount = b.sLayerInfo[i].iNalCount; o->sLayerInfo[i].pNalLengthInByte = b.sLayerInfo[i].pNalLengthInByte;
       o->sLayerInfo[i].pBsBuf = b.sLayerInfo[i].pBsBuf;
+    }
+    // rPsnr of the picture's VCL layer entry, for the planes the picture asked for; every other entry stays 0 (pLayerBsInfo, encoder_ext.cpp:3959-3970)
+    if (pic_planes) {
+      WelsHipFrameQuality fq;
+      if (g_api.GetFrameQuality (m_p, &fq)) return cmUnknownReason;
+      for (int i = 0; i < b.iLayerNum; ++i)
+        if (b.sLayerInfo[i].uiLayerType == WELSHIP_VIDEO_CODING_LAYER)
+          for (int k = 0; k < 3; ++k) o->sLayerInfo[i].rPsnr[k] = ((pic_planes >> k) & 1) ? fq.rPsnr[k] : 0.0f;
     }
     if (!m_dump.empty() && b.eFrameType != WelsHipFrameTypeSkip) {   // ENCODER_OPTION_DUMP_FILE: the reconstructed pictures, appended
       std::vector<uint8_t> rec ((size_t)m_w * m_h * 3 / 2);
@@ -167,6 +184,7 @@ class CWelsHipEncoder : public ISVCEncoder {
   WelsHipEncoder* m_p = NULL;
   std::string m_dump;
   int m_w = 0, m_h = 0, m_frames = 0;
+  int m_param_planes = 0;             // SEncParamExt::bPsnrY / U / V as a plane mask
 };
 
 }  // namespace

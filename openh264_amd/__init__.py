@@ -25,6 +25,7 @@ HAS_INTER_PATH = True
 
 
 OPTION_DATAFORMAT, OPTION_IDR_INTERVAL, OPTION_FRAME_RATE, OPTION_COMPLEXITY = 0, 1, 4, 15     # ENCODER_OPTION ids
+OPTION_PSNR_PLANES = 0x10000                   # engine-private: quality statistic of the next pictures, bit mask 1 Y | 2 U | 4 V
 
 
 class SEncParamExt(C.Structure):
@@ -38,8 +39,14 @@ class SEncParamExt(C.Structure):
         ("bEnableFrameCroppingFlag", C.c_int32), ("iDLayerQp", C.c_int32), ("uiSliceMode", C.c_int32), ("uiSliceNum", C.c_int32),
         ("bEnableAdaptiveQuant", C.c_int32), ("bEnableBackgroundDetection", C.c_int32), ("bEnableSceneChangeDetect", C.c_int32),
         ("bEnableLongTermReference", C.c_int32), ("bEnableDenoise", C.c_int32), ("bEnableFrameSkip", C.c_int32),
-        ("iDevice", C.c_int32), ("iMultipleThreadIdc", C.c_int32), ("reserved", C.c_int32 * 6), ("uiSliceMbNum", C.c_uint32 * 35),
+        ("iDevice", C.c_int32), ("iMultipleThreadIdc", C.c_int32), ("bPsnrY", C.c_int32), ("bPsnrU", C.c_int32), ("bPsnrV", C.c_int32),
+        ("reserved", C.c_int32 * 3), ("uiSliceMbNum", C.c_uint32 * 35),
     ]
+
+
+class WelsHipFrameQuality(C.Structure):
+    """Per-picture quality statistic: SSE and the reference's PSNR per plane (Y, U, V); planes not measured report 0."""
+    _fields_ = [("uiSse", C.c_uint64 * 3), ("rPsnr", C.c_float * 3), ("uiPlanes", C.c_uint32)]
 
 
 class SSourcePicture(C.Structure):
@@ -87,6 +94,8 @@ def load_library(path=None):
     lib.WelsHipBackendName.argtypes = [C.c_void_p]
     lib.WelsHipBackendName.restype = C.c_char_p
     lib.WelsHipGetLastError.restype = C.c_char_p
+    lib.WelsHipGetFrameQuality.argtypes = [C.c_void_p, C.POINTER(WelsHipFrameQuality)]
+    lib.WelsHipGroupGetFrameQuality.argtypes = [C.c_void_p, C.POINTER(WelsHipFrameQuality)]
     _libs[path] = lib
     return lib
 
@@ -176,6 +185,15 @@ class Encoder:
             raise WelsHipError(rc, self._err())
         return bytes(buf)
 
+    def frame_quality(self):
+        """Quality statistic of the picture of the last EncodeFrame: (sse[3], psnr[3]) for Y, U, V -- the planes not requested (bPsnr*
+        parameters | OPTION_PSNR_PLANES) report 0 and 0.0; psnr is the float the reference reports in SLayerBSInfo::rPsnr."""
+        q = WelsHipFrameQuality()
+        rc = self._lib.WelsHipGetFrameQuality(self._h, C.byref(q))
+        if rc:
+            raise WelsHipError(rc, "frame_quality: no picture encoded yet")
+        return list(q.uiSse), list(q.rPsnr)
+
     def backend_name(self):
         return (self._lib.WelsHipBackendName(self._h) or b"").decode()
 
@@ -201,7 +219,8 @@ class Encoder:
 
 def encode_sequence(yuv_bytes, width, height, lib_path=None, stats=None, force_idr_at=-1, options_at=(), param_sets_at=-1, **params):
     """Convenience: encode a whole I420 sequence; returns (bitstream bytes, last recon frame).
-    `stats`: optional dict that receives developer statistics (overflow_reencodes);
+    `stats`: optional dict that receives developer statistics (overflow_reencodes) and, when a plane's quality statistic is requested (bPsnrY / U / V
+    or OPTION_PSNR_PLANES in `options_at`), "quality": one (sse[3], psnr[3]) per picture (Encoder.frame_quality);
     `force_idr_at`: ForceIntraFrame(true) is called before that frame index;
     `options_at`: (frame index, option id, value) triples -> SetOption before that frame."""
     enc = Encoder(lib_path)
@@ -219,6 +238,8 @@ def encode_sequence(yuv_bytes, width, height, lib_path=None, stats=None, force_i
         raise WelsHipError(rc, enc.last_error())
     fsz = width * height * 3 // 2
     out = bytearray()
+    want_quality = bool(p.bPsnrY or p.bPsnrU or p.bPsnrV) or any(oid == OPTION_PSNR_PLANES and val for _, oid, val in options_at)
+    quality = []
     for i in range(len(yuv_bytes) // fsz):
         if i == force_idr_at:
             enc.ForceIntraFrame(True)
@@ -234,9 +255,13 @@ def encode_sequence(yuv_bytes, width, height, lib_path=None, stats=None, force_i
         if rc:
             raise WelsHipError(rc, enc.last_error())
         out += bs
+        if want_quality:
+            quality.append(enc.frame_quality())
     recon = enc.GetReconFrame()
     if stats is not None:
         stats["overflow_reencodes"] = enc.overflow_reencodes()
+        if want_quality:
+            stats["quality"] = quality
     enc.Uninitialize()
     enc.close()
     return bytes(out), recon
@@ -375,6 +400,15 @@ class EncoderGroup:
         if rc:
             raise WelsHipError(rc, (self._lib.WelsHipGetLastError() or b"").decode())
         return dict(total_ms=out[0], md_ms=out[1], deblock_ms=out[2], expand_ms=out[3])
+
+    def frame_quality(self):
+        """Quality statistic of every session's picture of the step whose bitstreams were returned last (encode_frames, step, or a
+        finished encode_frames_pipelined): a list of (sse[3], psnr[3]), one per session."""
+        q = (WelsHipFrameQuality * self.n)()
+        rc = self._lib.WelsHipGroupGetFrameQuality(self._h, q)
+        if rc:
+            raise WelsHipError(rc, "frame_quality: no step finished yet")
+        return [(list(x.uiSse), list(x.rPsnr)) for x in q]
 
     def host_stats(self):
         """Host share of the complete frame steps so far (thread time per picture)."""

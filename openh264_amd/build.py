@@ -5,7 +5,7 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "openh264_amd", "csrc")
-HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("encoder.cpp", "frame_api.cpp", "entropy_cavlc.cpp", "headers.cpp")]
+HOST_SRCS = [os.path.join(CSRC, "host", f) for f in ("encoder.cpp", "frame_api.cpp", "entropy_cavlc.cpp", "headers.cpp", "quality.cpp")]
 # (csrc/hip/leaf.hip is the second half of prims.hip's translation unit: the kernels both layers launch are compiled once)
 HIP_SRCS = [os.path.join(CSRC, "hip", "hip_backend.hip"), os.path.join(CSRC, "hip", "prims.hip"), os.path.join(CSRC, "hip", "downsample.hip")]
 LIB = os.path.join(ROOT, "openh264_amd", "libwelship.so")

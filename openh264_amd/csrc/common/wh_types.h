@@ -189,7 +189,7 @@ typedef struct WhPicJob {
   // coded again after a CAVLC overflow) -- the reference's first pass has overwritten its entry by then (WelsMdInterSaveSadAndRefMbType).
   int32_t*       sad_cost0_out;
   int32_t        dyn_redo;
-  int32_t        pad5;
+  uint32_t       sse_planes;  // quality statistic (kernels/quality_pic.h, Backend::run_sse): planes to measure, bit 0 Y, 1 U, 2 V; 0 = none
   // Tiled twins of the border-expanded planes (WH_TILE_*, below): what the search windows of the P kernel are fetched from.
   // [0] luma, [1] Cb and Cr interleaved.  rec_tiles is written by the pass that makes a picture a reference (border expansion,
   // Backend::run_expand), ref_tiles is the reference picture's; both NULL-free whenever rec / ref are.
@@ -200,6 +200,8 @@ typedef struct WhPicJob {
   // deblocking pass read it from here, and the deblocking pass writes every sample of rec[] exactly once, filtered or not.  A planar
   // picture costs both passes 32 pieces of 32 different lines per macroblock.  NULL: no deblocking pass follows, rec[] is written directly.
   uint8_t*       rec_blk;
+  uint64_t*      sse;         // sse_planes != 0: this picture's three words {Y, U, V} (zeroed by the host), where run_sse adds the sum of squared
+                              //   differences between src[0] and the final rec[] over the macroblock-aligned picture; else NULL
 } WhPicJob;
 
 // ---- tiled reference pictures ------------------------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "../kernels/vaa_pic.h"
 #include "../kernels/bgd_pic.h"
 #include "../kernels/scene_pic.h"
+#include "../kernels/quality_pic.h"
 #include "../common/compact.h"
 
 namespace {
@@ -944,6 +945,14 @@ __global__ __launch_bounds__ (64) void k_scene (WhSeqParams P, const WhPicJob* j
   wh_scene_mb_body (P, J, (int) (blockIdx.x % (unsigned)P.mb_w), (int) (blockIdx.x / (unsigned)P.mb_w));
 }
 
+// Quality statistic (kernels/quality_pic.h): one wavefront per macroblock row, four rows per workgroup, grid y = pictures.
+__global__ __launch_bounds__ (256) void k_sse (WhSeqParams P, const WhPicJob* jobs) {
+  const WhPicJob J = jobs[blockIdx.y];
+  const int row = (int)blockIdx.x * 4 + __builtin_amdgcn_readfirstlane ((int)threadIdx.x >> 6);
+  if (row >= P.mb_h || !J.sse_planes || !J.sse) return;
+  wh_sse_row_body (P, J, row);
+}
+
 // QP_Y chain for the deblocking filter of pictures with a per-MB QP map: one wavefront per (slice, picture).
 __global__ __launch_bounds__ (64) void k_qp_chain (WhSeqParams P, const WhPicJob* jobs) {
   const WhPicJob J = jobs[blockIdx.y];
@@ -1210,6 +1219,11 @@ class HipBackend : public wh::Backend {
   }
   void run_scene (const WhSeqParams& P, const WhPicJob* jobs, int n) override {
     hipLaunchKernelGGL (k_scene, dim3 (P.mb_w * P.mb_h, n), dim3 (64), 0, stream_, P, jobs);
+    HIP_TRY (hipGetLastError());
+  }
+  void run_sse (const WhSeqParams& P, const WhPicJob* jobs, int n) override {
+    if (P.mb_w > WH_SSE_MAX_MB_W) { note_error (hipErrorInvalidValue, "run_sse: picture wider than the per-lane sums allow", __LINE__); return; }
+    hipLaunchKernelGGL (k_sse, dim3 ((P.mb_h + 3) / 4, n), dim3 (256), 0, stream_, P, jobs);
     HIP_TRY (hipGetLastError());
   }
   void run_qp_chain (const WhSeqParams& P, const WhPicJob* jobs, int n) override {

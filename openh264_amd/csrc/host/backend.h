@@ -44,6 +44,10 @@ class Backend {
   virtual void run_deblock (const WhSeqParams& P, const WhPicJob* jobs, int n) = 0;   // in-loop filter on rec[]
   virtual void run_expand (const WhSeqParams& P, const WhPicJob* jobs, int n) = 0;    // make rec[] a reference: replicate its borders (32/16 px), write its tiled twin rec_tiles[]
   virtual void run_compact (const WhSeqParams& P, const WhPicJob* jobs, int n) = 0;   // pack records[] into compact / compact_off (common/compact.h)
+  // quality statistic (kernels/quality_pic.h): every picture with sse_planes != 0 adds its per-plane sum of squared differences between src[0]
+  // and the final rec[] to its sse[] words (zeroed by the caller).  Issued after the last pass that writes rec[] (deblocking or expansion).
+  // Default body (host/quality.cpp): the wave emulation of the kernel in the CPU test build; the HIP backend launches the kernel.
+  virtual void run_sse (const WhSeqParams& P, const WhPicJob* jobs, int n);
   // Independent in-order queues (HIP streams): everything issued after select_queue (k) goes to queue k; work on
   // different queues may overlap on the device.  sync() waits for all of them and returns 0, or the number of
   // in-kernel dependency waits that timed out since the last sync (the pictures of that step are then invalid).

@@ -9,6 +9,7 @@
 // batched launch set per frame step covers all N pictures, which is how a single MI355X is filled
 // (independent sessions / simulcast layers / all-IDR frames have no mutual dependency).
 #include "encoder_internal.h"
+#include "quality.h"
 using wh::align_up; using wh::rec_blocks_on; using wh::DevPicture;
 
 namespace wh {
@@ -97,6 +98,19 @@ struct SessionCore {
   // brings all of them), owned by the group
   uint32_t* x_doff[WH_PIPE_MAX_AHEAD + 1] = {};
   uint32_t* x_hoff[WH_PIPE_MAX_AHEAD + 1] = {};
+  // ---- per-picture quality statistic (kernels/quality_pic.h): which planes, and where a picture's three SSE words go ----
+  uint32_t psnr_opt = 0;              // WELSHIP_OPTION_PSNR_PLANES (ORed with the parameters' bPsnr* flags)
+  uint32_t psnr_planes() const { return ((prm.bPsnrY ? 1u : 0u) | (prm.bPsnrU ? 2u : 0u) | (prm.bPsnrV ? 4u : 0u) | psnr_opt) & 7u; }
+  uint64_t* d_sse_n[WH_PIPE_MAX_AHEAD + 1] = {};   // per buffer set: this session's {Y, U, V} words on the device (slices of the owner's array) ...
+  uint64_t* h_sse_n[WH_PIPE_MAX_AHEAD + 1] = {};   // ... and their page-locked host copies; owned by the encoder / group
+  WelsHipFrameQuality quality;        // of the last picture whose bitstream was returned
+  bool have_quality = false;
+  void note_quality (int buf, uint32_t planes) {
+    static const uint64_t none[3] = {0, 0, 0};
+    // (the reference's area: the picture rounded up to whole macroblocks, kernels/quality_pic.h)
+    wh::fill_quality (&quality, h_sse_n[buf] ? h_sse_n[buf] : none, planes, mb_w * 16, mb_h * 16);
+    have_quality = true;
+  }
 
   static int validate (const WelsHipEncParam* p) {
     // same spirit as ParamValidationExt (encoder_ext.cpp:403-680)
@@ -482,6 +496,8 @@ struct SessionCore {
     job->db_flags = d_dbflags;
     if (++db_gen == 0) db_gen = 1;
     job->db_gen = db_gen;
+    job->sse_planes = d_sse_n[pbuf] ? psnr_planes() : 0;
+    job->sse = job->sse_planes ? d_sse_n[pbuf] : nullptr;
     if (qp_map_in_use) { memset (h_mb_ctl.data(), 0, sizeof (WhMbCtl) * h_mb_ctl.size()); qp_map_in_use = false; }
     cur_job = *job;
     return WELSHIP_OK;
@@ -731,12 +747,14 @@ struct SessionCore {
 static WhSeqParams plain_seq (const WhSeqParams& s) { WhSeqParams q = s; if (q.flags == 0) q.flags |= WH_SEQ_PLAIN; return q; }
 
 // Run the device part of one frame step for `n` pictures described by the device array d_jobs.
-void run_device_step (wh::Backend* be, const WhSeqParams& s, const WhPicJob* d_jobs, int n, bool idr, bool need_ref, bool qp_map = false) {
+// `sse`: the pictures' quality statistic follows the last pass that writes rec[] (their sse words zeroed by the caller).
+void run_device_step (wh::Backend* be, const WhSeqParams& s, const WhPicJob* d_jobs, int n, bool idr, bool need_ref, bool qp_map = false, bool sse = false) {
   if (idr) be->run_intra (s, d_jobs, n);
   else be->run_inter (s, d_jobs, n);
   if (qp_map && s.deblock_idc != 1) be->run_qp_chain (s, d_jobs, n);
   if (s.deblock_idc != 1) be->run_deblock (s, d_jobs, n);
   if (need_ref) be->run_expand (s, d_jobs, n);
+  if (sse) be->run_sse (s, d_jobs, n);
 }
 
 // One round of the overflow loop for the picture session `c` is working on: raise the QP of the offending macroblock,
@@ -746,8 +764,11 @@ int reencode_after_overflow (wh::Backend* be, SessionCore& c, WhPicJob* d_job) {
   const int rc = c.retry_after_overflow (&job);
   if (rc) return rc;
   be->upload (d_job, &job, sizeof (job));
-  run_device_step (be, c.seq, d_job, 1, c.cur_idr, c.prm.uiIntraPeriod != 1, true);
+  const bool q = job.sse_planes != 0;          // the statistic of the picture's final reconstruction (buffer set 0: not a pipelined group)
+  if (q) be->fill (job.sse, 0, 3 * sizeof (uint64_t));
+  run_device_step (be, c.seq, d_job, 1, c.cur_idr, c.prm.uiIntraPeriod != 1, true, q);
   be->download (c.h_records.data(), c.d_records, sizeof (WhMbRecord) * c.num_mb);
+  if (q) be->download (c.h_sse_n[0], job.sse, 3 * sizeof (uint64_t));
   if (be->sync()) { set_err ("device scheduler timed out; the picture was not encoded"); return WELSHIP_ERR_UNKNOWN; }
   return WELSHIP_OK;
 }
@@ -759,6 +780,8 @@ struct WelsHipEncoder {
   bool inited = false;
   SessionCore core;
   WhPicJob* d_job = nullptr;
+  uint64_t* d_sse = nullptr;          // the quality statistic of the picture being coded (SessionCore::d_sse_n[0])
+  WhHostVec<uint64_t> h_sse;
 };
 
 struct WelsHipEncoderGroup {
@@ -805,6 +828,31 @@ struct WelsHipEncoderGroup {
   bool mixed = false;                           // sessions disagree (scene changes, forced IDRs): each queue chunk of
   std::vector<int> order;                       //   d_jobs holds its P pictures first, then its IDR pictures;
   std::vector<int> chunk_p;                     //   order[k] = session of job slot k, chunk_p[q] = P pictures of chunk q
+  // quality statistic: [session][Y, U, V] words per buffer set -- one fill, one pass per launch chunk and one copy per step -- and the
+  // values of the step whose bitstreams were returned last
+  uint64_t* d_sse_all[WH_PIPE_MAX_AHEAD + 1] = {};
+  WhHostVec<uint64_t> h_sse_all[WH_PIPE_MAX_AHEAD + 1];
+  std::vector<WelsHipFrameQuality> quality;
+  bool have_quality = false;
+  uint32_t sse_planes() const { return sess[0]->psnr_planes(); }      // (the sessions share their parameters)
+  bool alloc_sse (int b) {
+    const size_t words = 3 * sess.size();
+    d_sse_all[b] = (uint64_t*)be->alloc (sizeof (uint64_t) * words);
+    if (!d_sse_all[b]) return false;
+    h_sse_all[b].assign (words, 0);
+    be->pin_host (h_sse_all[b].data(), sizeof (uint64_t) * words);
+    for (size_t i = 0; i < sess.size(); ++i) { sess[i]->d_sse_n[b] = d_sse_all[b] + 3 * i; sess[i]->h_sse_n[b] = h_sse_all[b].data() + 3 * i; }
+    return true;
+  }
+  void take_quality (bool pipelined_step) {
+    quality.resize (sess.size());
+    for (size_t i = 0; i < sess.size(); ++i) {
+      SessionCore& c = *sess[i];
+      if (pipelined_step) c.note_quality (c.fin.buf, c.fin.job.sse_planes); else c.note_quality (0, c.cur_job.sse_planes);
+      quality[i] = c.quality;
+    }
+    have_quality = true;
+  }
 };
 
 extern "C" {
@@ -824,6 +872,10 @@ int WelsHipUninitialize (WelsHipEncoder* e) {
     e->core.release();
     if (e->d_job) e->be->free (e->d_job);
     e->d_job = nullptr;
+    if (e->d_sse) e->be->free (e->d_sse);
+    e->d_sse = nullptr;
+    if (!e->h_sse.empty()) e->be->unpin_host (e->h_sse.data());
+    e->h_sse.clear();
     delete e->be;
     e->be = nullptr;
   }
@@ -863,7 +915,13 @@ int WelsHipInitializeExt (WelsHipEncoder* e, const WelsHipEncParam* p) {
   rc = e->core.init (e->be, p, 2);
   if (rc) { e->core.release(); delete e->be; e->be = nullptr; return rc; }
   e->d_job = (WhPicJob*)e->be->alloc (sizeof (WhPicJob));
-  if (!e->d_job) { set_err ("out of device memory"); e->core.release(); delete e->be; e->be = nullptr; return WELSHIP_ERR_MEMORY; }
+  e->d_sse = (uint64_t*)e->be->alloc (3 * sizeof (uint64_t));
+  if (e->d_sse) {
+    e->h_sse.assign (3, 0);
+    e->be->pin_host (e->h_sse.data(), 3 * sizeof (uint64_t));
+    e->core.d_sse_n[0] = e->d_sse; e->core.h_sse_n[0] = e->h_sse.data();
+  }
+  if (!e->d_job || !e->d_sse) { set_err ("out of device memory"); WelsHipUninitialize (e); return WELSHIP_ERR_MEMORY; }
   e->inited = true;
   return WELSHIP_OK;
 }
@@ -916,6 +974,12 @@ int WelsHipSetOption (WelsHipEncoder* e, int id, void* opt) {
   }
   case WELSHIP_OPTION_TRACE_LEVEL: case WELSHIP_OPTION_TRACE_CALLBACK: case WELSHIP_OPTION_TRACE_CALLBACK_CONTEXT:
     return WELSHIP_OK;
+  case WELSHIP_OPTION_PSNR_PLANES: {         // the quality statistic of the next pictures (SSourcePicture::bPsnr* of the reference)
+    const int32_t v = * (int32_t*)opt;
+    if (v < 0 || v > 7) { set_err ("the plane mask takes bits 0 (Y), 1 (U) and 2 (V) only"); return WELSHIP_ERR_INIT_PARA; }
+    c.psnr_opt = (uint32_t)v;
+    return WELSHIP_OK;
+  }
   default:
     set_err ("option not supported by this engine");
     return WELSHIP_ERR_UNSUPPORTED;
@@ -930,6 +994,7 @@ int WelsHipGetOption (WelsHipEncoder* e, int id, void* opt) {
   case WELSHIP_OPTION_IDR_INTERVAL: * (int32_t*)opt = (int32_t)c.prm.uiIntraPeriod; return WELSHIP_OK;
   case WELSHIP_OPTION_FRAME_RATE: * (float*)opt = c.prm.fMaxFrameRate; return WELSHIP_OK;
   case WELSHIP_OPTION_COMPLEXITY: * (int32_t*)opt = c.prm.iComplexityMode; return WELSHIP_OK;
+  case WELSHIP_OPTION_PSNR_PLANES: * (int32_t*)opt = (int32_t)c.psnr_opt; return WELSHIP_OK;
   default: return WELSHIP_ERR_INIT_PARA;     // the reference's GetOption: unknown id -> cmInitParaError
   }
 }
@@ -955,8 +1020,11 @@ int WelsHipEncodeFrame (WelsHipEncoder* e, const WelsHipSourcePicture* src, Wels
   }
   { const int brc = c.begin_frame (slot, &job); if (brc) return brc; }
   e->be->upload (e->d_job, &job, sizeof (job));
-  run_device_step (e->be, c.seq, e->d_job, 1, c.cur_idr, c.prm.uiIntraPeriod != 1);
+  const bool q = job.sse_planes != 0;        // quality statistic: 24 bytes come back with the records
+  if (q) e->be->fill (c.d_sse_n[0], 0, 3 * sizeof (uint64_t));
+  run_device_step (e->be, c.seq, e->d_job, 1, c.cur_idr, c.prm.uiIntraPeriod != 1, false, q);
   e->be->download (c.h_records.data(), c.d_records, sizeof (WhMbRecord) * c.num_mb);
+  if (q) e->be->download (c.h_sse_n[0], c.d_sse_n[0], 3 * sizeof (uint64_t));
   if (e->be->sync()) { set_err ("device scheduler timed out; the picture was not encoded"); return WELSHIP_ERR_UNKNOWN; }
   c.upload_pending = false;
   int rc = c.finish_frame (out, src->uiTimeStamp);
@@ -965,7 +1033,14 @@ int WelsHipEncodeFrame (WelsHipEncoder* e, const WelsHipSourcePicture* src, Wels
     if (rc) return rc;
     rc = c.finish_frame (out, src->uiTimeStamp);
   }
+  if (rc == WELSHIP_OK) c.note_quality (0, job.sse_planes);     // (a re-encode measured the final reconstruction again)
   return rc;
+}
+
+int WelsHipGetFrameQuality (WelsHipEncoder* e, WelsHipFrameQuality* q) {
+  if (!e || !e->inited || !q || !e->core.have_quality) return WELSHIP_ERR_INIT_PARA;
+  *q = e->core.quality;
+  return WELSHIP_OK;
 }
 
 int WelsHipGetReconFrame (WelsHipEncoder* e, uint8_t* dst, size_t bytes) {
@@ -1019,6 +1094,7 @@ int WelsHipGroupCreate (WelsHipEncoderGroup** pp, const WelsHipEncParam* p, int 
   g->d_jobs = (WhPicJob*)be->alloc (sizeof (WhPicJob) * n_sessions);
   if (!g->d_jobs) { set_err ("out of device memory"); for (auto& s : g->sess) s->release(); delete be; delete g; return WELSHIP_ERR_MEMORY; }
   g->h_jobs.resize (n_sessions);
+  if (!g->alloc_sse (0)) { set_err ("out of device memory"); WelsHipGroupDestroy (g); return WELSHIP_ERR_MEMORY; }
   *pp = g;
   return WELSHIP_OK;
 }
@@ -1037,6 +1113,10 @@ void WelsHipGroupDestroy (WelsHipEncoderGroup* g) {
     }
     for (void* e : g->dl_ev) g->be->event_destroy (e);
     if (g->d_job_aux) g->be->free (g->d_job_aux);
+    for (int b = 0; b <= WH_PIPE_MAX_AHEAD; ++b) {
+      if (g->d_sse_all[b]) g->be->free (g->d_sse_all[b]);
+      if (!g->h_sse_all[b].empty()) g->be->unpin_host (g->h_sse_all[b].data());
+    }
   }
   g->be->free (g->d_jobs);
   delete g->be;
@@ -1095,6 +1175,7 @@ int WelsHipGroupBegin (WelsHipEncoderGroup* g, int slot) {
     for (int j = a; j < b; ++j) g->h_jobs[j] = jobs[g->order[j]];
     g->be->select_queue (q);
     g->be->upload (g->d_jobs + a, g->h_jobs.data() + a, sizeof (WhPicJob) * (b - a));
+    if (g->sse_planes()) g->be->fill (g->d_sse_all[0] + 3 * (size_t)a, 0, sizeof (uint64_t) * 3 * (size_t) (b - a));     // the chunk's quality words
   }
   return WELSHIP_OK;
 }
@@ -1112,6 +1193,7 @@ int WelsHipGroupRunDevice (WelsHipEncoderGroup* g, int wait) {
     if (c0.use_compact) g->be->run_compact (s, g->d_jobs + a, b - a);
     if (s.deblock_idc != 1) g->be->run_deblock (s, g->d_jobs + a, b - a);
     if (c0.prm.uiIntraPeriod != 1) g->be->run_expand (s, g->d_jobs + a, b - a);
+    if (g->sse_planes()) g->be->run_sse (s, g->d_jobs + a, b - a);
   }
   if (wait && g->be->sync()) { set_err ("device scheduler timed out"); return WELSHIP_ERR_UNKNOWN; }
   return WELSHIP_OK;
@@ -1127,6 +1209,12 @@ int WelsHipGroupFinish (WelsHipEncoderGroup* g, WelsHipFrameBSInfo* outs) {
     if (packed) g->be->download (c.h_compact_off.data(), c.d_compact_off, sizeof (uint32_t) * ((size_t)c.num_mb + 1));
     else g->be->download (c.h_records.data(), c.d_records, sizeof (WhMbRecord) * c.num_mb);
   }
+  if (g->sse_planes())      // the quality words of the step: one copy per launch chunk
+    for (int q = 0; q < g->queues; ++q) {
+      const size_t a = (size_t)g->chunk_first (q), b = (size_t)g->chunk_first (q + 1);
+      g->be->select_queue (q);
+      g->be->download (g->h_sse_all[0].data() + 3 * a, g->d_sse_all[0] + 3 * a, sizeof (uint64_t) * 3 * (b - a));
+    }
   if (g->be->sync()) { set_err ("device scheduler timed out; the step was not encoded"); return WELSHIP_ERR_UNKNOWN; }
   if (packed) {        // the sizes are known now: the packed records themselves
     for (int i = 0; i < n; ++i) {
@@ -1165,6 +1253,7 @@ int WelsHipGroupFinish (WelsHipEncoderGroup* g, WelsHipFrameBSInfo* outs) {
                                                                              : ": entropy coding of the frame failed"));
     return rcs[i];
   }
+  g->take_quality (false);
   return WELSHIP_OK;
 }
 
@@ -1241,6 +1330,7 @@ int WelsHipGroupSetPipelined (WelsHipEncoderGroup* g, int ahead) {
   }
   g->d_job_aux = (WhPicJob*)g->be->alloc (sizeof (WhPicJob));
   if (!g->d_job_aux) { set_err ("out of device memory"); return WELSHIP_ERR_MEMORY; }
+  for (int b = 1; b < depth; ++b) if (!g->alloc_sse (b)) { set_err ("out of device memory"); return WELSHIP_ERR_MEMORY; }
   g->dl_ev.assign (n, nullptr);
   for (int i = 0; i < n; ++i) g->dl_ev[i] = g->be->event_create();
   if (g->be->sync()) { set_err ("device error while setting up the pipelined group"); return WELSHIP_ERR_UNKNOWN; }
@@ -1294,6 +1384,8 @@ int pipe_submit (WelsHipEncoderGroup* g, const WelsHipSourcePicture* srcs, doubl
   be->queue_wait_event (0, g->up_ev[0][sb]);            // the kernels wait (on the device) for this step's sources
   if (upq[1] != upq[0]) be->queue_wait_event (0, g->up_ev[1][sb]);
   be->upload (dj, hj.data(), sizeof (WhPicJob) * n);
+  const bool sse = g->sse_planes() != 0;
+  if (sse) be->fill (g->d_sse_all[sb], 0, sizeof (uint64_t) * 3 * (size_t)n);     // (its previous step's copy finished in an earlier call)
   const WhSeqParams& s = c0.seq;
   be->run_src_tile_jobs (s, dj, n);
   if (np) be->run_inter (plain_seq (s), dj, np);
@@ -1301,7 +1393,8 @@ int pipe_submit (WelsHipEncoderGroup* g, const WelsHipSourcePicture* srcs, doubl
   be->run_compact (s, dj, n);
   if (s.deblock_idc != 1) be->run_deblock (s, dj, n);
   if (c0.prm.uiIntraPeriod != 1) be->run_expand (s, dj, n);
-  be->event_record (g->step_ev[sb]);                    // what the download queue will wait for before it copies this step's records
+  if (sse) be->run_sse (s, dj, n);
+  be->event_record (g->step_ev[sb]);                    // what the download queue will wait for before it copies this step's records (and quality words)
   for (auto& c : g->sess) c->submit_advance();
   ++g->step_no;
   tm[2] = now();
@@ -1318,6 +1411,7 @@ int pipe_finish (WelsHipEncoderGroup* g, WelsHipFrameBSInfo* outs, std::vector<i
   const size_t off_words = (size_t)g->sess[0]->num_mb + 1;
   be->queue_wait_event (WH_PIPE_DLQ, g->step_ev[fb]);   // that step's kernels, not the later steps'
   be->download_on (WH_PIPE_DLQ, g->h_off_all[fb].data(), g->d_off_all[fb], sizeof (uint32_t) * off_words * n);
+  if (g->sess[0]->fin.job.sse_planes) be->download_on (WH_PIPE_DLQ, g->h_sse_all[fb].data(), g->d_sse_all[fb], sizeof (uint64_t) * 3 * (size_t)n);
   if (be->sync_queue (WH_PIPE_DLQ) || be->peek_queue_errors (0, WH_PIPE_DLQ)) { set_err ("device scheduler timed out; the step was not encoded"); return WELSHIP_ERR_UNKNOWN; }
   tm[3] = now();
   for (int i = 0; i < n; ++i) {
@@ -1356,6 +1450,7 @@ int pipe_rerun (WelsHipEncoderGroup* g, SessionCore& c, WhPicJob* job, bool idr)
   be->run_compact (c.seq, g->d_job_aux, 1);
   if (c.seq.deblock_idc != 1) be->run_deblock (c.seq, g->d_job_aux, 1);
   if (c.prm.uiIntraPeriod != 1) be->run_expand (c.seq, g->d_job_aux, 1);
+  if (job->sse_planes) { be->fill (job->sse, 0, 3 * sizeof (uint64_t)); be->run_sse (c.seq, g->d_job_aux, 1); }     // (copied back when its step is finished)
   if (be->sync()) { set_err ("device scheduler timed out; the picture was not encoded"); return WELSHIP_ERR_UNKNOWN; }
   return WELSHIP_OK;
 }
@@ -1416,8 +1511,10 @@ int WelsHipGroupEncodeFramesPipelined (WelsHipEncoderGroup* g, const WelsHipSour
         if (rcs[i]) break;
         job.src[1] = nullptr;
         be->upload (g->d_job_aux, &job, sizeof (job));
-        run_device_step (be, c.seq, g->d_job_aux, 1, c.fin.idr, need_ref, true);
+        if (job.sse_planes) be->fill (job.sse, 0, 3 * sizeof (uint64_t));
+        run_device_step (be, c.seq, g->d_job_aux, 1, c.fin.idr, need_ref, true, job.sse_planes != 0);
         be->download (c.h_records.data(), c.d_records, sizeof (WhMbRecord) * c.num_mb);
+        if (job.sse_planes) be->download (c.h_sse_n[c.fin.buf], job.sse, 3 * sizeof (uint64_t));
         if (be->sync()) { set_err ("device scheduler timed out; the picture was not encoded"); rcs[i] = WELSHIP_ERR_UNKNOWN; break; }
         rcs[i] = c.entropy_frame (outs ? &outs[i] : nullptr, 0, false, c.fin.idr, c.fin.frame_num, nullptr, nullptr);
       }
@@ -1431,6 +1528,7 @@ int WelsHipGroupEncodeFramesPipelined (WelsHipEncoderGroup* g, const WelsHipSour
                                                                                : ": entropy coding of the frame failed"));
       return rcs[i];
     }
+    g->take_quality (true);
     if (pFinished) *pFinished = 1;
   }
   if (srcs && src_rc) return src_rc;
@@ -1443,6 +1541,12 @@ int WelsHipGroupGetReconFrame (WelsHipEncoderGroup* g, int session, uint8_t* dst
 }
 
 const char* WelsHipGroupBackendName (WelsHipEncoderGroup* g) { return g ? g->be->name() : "none"; }
+
+int WelsHipGroupGetFrameQuality (WelsHipEncoderGroup* g, WelsHipFrameQuality* q) {
+  if (!g || !q || !g->have_quality) return WELSHIP_ERR_INIT_PARA;
+  for (size_t i = 0; i < g->quality.size(); ++i) q[i] = g->quality[i];
+  return WELSHIP_OK;
+}
 
 // Advance every session by one frame step on the device only (no D2H, no entropy coding): what the
 // hot-path benchmark times.  Stream state (frame type, reference swap) advances exactly as in Finish.
@@ -1489,6 +1593,7 @@ int WelsHipGroupBench (WelsHipEncoderGroup* g, int steps, int warmup, double* ou
       if (q == 0) be->event_record (ev[i * 4 + 2]);
       if (need_ref) be->run_expand (s, g->d_jobs + a, cnt);
       if (q == 0) be->event_record (ev[i * 4 + 3]);
+      if (g->sse_planes()) be->run_sse (s, g->d_jobs + a, cnt);      // (in the total only; WelsHipGroupBegin zeroed the words)
     }
     for (auto& c : g->sess) { c->pic[c->cur].is_p = !c->cur_idr; c->have_recon = true; ++c->frame_index; c->frame_num = (c->frame_num + 1) & 0x7fff; c->cur = c->next_of (c->cur); }
   }
